@@ -21,6 +21,9 @@ the previous stage sends (``--calib stage``, default; ``--calib full`` builds + 
 full model on every rank and cuts the stage, bit-identical INT8 weights for every split).
 Data: random prompt ids.  ``--device cpu --model tiny:llama``
 exercises the same code paths on CPU (gloo) for tests.
+A plain run sets up, warms up, times ``--steps`` steps and prints the result line; ``--full`` adds
+the side points that take decode runs of their own (batch-1 latency point, one-lane point), and
+``--dump-outputs DIR`` writes what the timed path computed (``dump_outputs``) for comparing builds.
 """
 from __future__ import annotations
 
@@ -91,10 +94,19 @@ def parse(argv=None):
                     help="N > 1: split the LM head by vocabulary over every rank (each rank its logits slice + "
                          "sampler phase 1, rank 0 the merge) instead of the whole head on the last stage; one "
                          "more micro-batch group in flight (parallel/vocab_head.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline run also measure the side points that take decode runs of their own "
+                         "(single GPU: the batch-1 latency point, see --latency-point, and the one-lane point of "
+                         "the same micro-batch); off by default: a plain run only sets up, warms up, times "
+                         "--steps steps and prints the result line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the timed path computed as DIR/<name>.npy (float32): "
+                         "the token ids every sequence received, those of the last timed step, and a fixed seeded "
+                         "sample of rows of the logits the decode forward gives on the final state")
     ap.add_argument("--latency-point", default="auto", choices=["auto", "off", "int8", "both"],
-                    help="also report batch-1 p50 per-token latency (single GPU): int8 = the benchmark model at "
-                         "micro-batch 1, both = plus a bf16 copy of the model (13.5 GB more, built for this only); "
-                         "auto = int8 on a GPU, off on CPU")
+                    help="with --full, also report batch-1 p50 per-token latency (single GPU): int8 = the benchmark "
+                         "model at micro-batch 1, both = plus a bf16 copy of the model (13.5 GB more, built for this "
+                         "only); auto = int8 on a GPU, off on CPU")
     ap.add_argument("--prefill-chunk", type=int, default=None,
                     help="chunked prefill size with HeadInfer (default: the whole prompt in one chunk)")
     ap.add_argument("--headinfer-heads", type=int, default=None,
@@ -233,14 +245,17 @@ def run_single(args):
     lmax = lat[-1] if lat else p50
     tokens = B * L * args.steps
     mem = torch.cuda.max_memory_allocated() / 1e9 if device.type == "cuda" else 0.0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, lanes, args.seed)
     kv_gpu = (kv.gpu_bytes() if kv is not None else gen_kv_bytes(gen)) / 1e9
     graphs = lanes[0]._run["graphs_ok"]
     del gen, lanes
     if device.type == "cuda":
         torch.cuda.empty_cache()
-    lat_pts = latency_points(args, device, model, cfg) if args.headinfer_heads is None else {}
+    # side points with decode runs of their own: only under --full
+    lat_pts = latency_points(args, device, model, cfg) if args.full and args.headinfer_heads is None else {}
     one_lane = {}
-    if L > 1 and device.type == "cuda" and args.latency_point != "off":
+    if args.full and L > 1 and device.type == "cuda" and args.latency_point != "off":
         # the same micro-batch in ONE lane: the latency side of the lanes trade-off
         one_lane = dict(micro_batch=B, lanes=1, steps=min(args.steps, 20),
                         **batch1_p50(model, cfg, args, device, min(args.steps, 20), rows=B))
@@ -253,6 +268,43 @@ def run_single(args):
                 prefill_tps=B * L * args.prompt_len / prefill_s, build_s=t_build, graphs=graphs,
                 mem_gb=mem, partition=[0, cfg.num_layers], ttft_ms=ttft_ms, world_size=1, kv_gpu_gb=kv_gpu,
                 kv_host_gb=(kv.host_bytes() / 1e9 if kv is not None else 0.0))
+
+
+DUMP_LOGIT_BYTES = 32 << 20     # --dump-outputs: cap of the logits sample (the whole dump stays far under 64 MB)
+
+
+@torch.no_grad()
+def dump_outputs(path, lanes, seed: int) -> None:
+    """``--dump-outputs``: what a caller of the timed decode path holds after its last step, as
+    float32 ``.npy`` files (token ids are exact in float32), rows in prompt order (lane major):
+
+    ``tokens``       [B, n]  every id sampled so far (prefill token, warm-up and timed steps)
+    ``last_tokens``  [B]     the ids the last timed step sampled
+    ``next_logits``  [R, V]  logits of one more eager decode forward over the final state (last
+                             token + KV cache of every step), for a fixed seeded sample of R rows
+    ``logit_rows``   [R]     the rows of that sample
+    """
+    import numpy as np
+    from edgellm.engine.generate import GRAPH_BUCKET
+    from edgellm.models.decoder import AttnCtx
+    os.makedirs(path, exist_ok=True)
+    toks, logits = [], []
+    for x in lanes:
+        r, st = x._run, x._state
+        toks.append(st.out[:, :r["produced"]].float().cpu())
+        B = r["B"]
+        max_len = r["host_max"] + 1
+        if r["graphs_ok"]:    # the length bucket the captured step of this position runs with
+            max_len = min(x.max_seq, ((max_len + GRAPH_BUCKET - 1) // GRAPH_BUCKET) * GRAPH_BUCKET)
+        ctx = AttnCtx("decode", B, 1, st.pos, st.seq_lens, max_len, x.kv.rows(0, B), x.rope,
+                      attn_hook=x.attn_hook, b1=x.b1 and B == 1)
+        logits.append(x.model(st.tok.view(B, 1), ctx).reshape(B, -1).float().cpu())
+    toks, logits = torch.cat(toks, 0), torch.cat(logits, 0)
+    n = max(1, min(logits.shape[0], DUMP_LOGIT_BYTES // (4 * logits.shape[1])))
+    rows = torch.randperm(logits.shape[0], generator=torch.Generator().manual_seed(seed))[:n].sort().values
+    for name, t in (("tokens", toks), ("last_tokens", toks[:, -1]), ("next_logits", logits[rows]),
+                    ("logit_rows", rows.float())):
+        np.save(os.path.join(path, name + ".npy"), t.contiguous().numpy())
 
 
 def kv_dtype(args, cfg) -> str:

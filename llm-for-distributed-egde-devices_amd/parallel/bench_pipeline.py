@@ -141,6 +141,15 @@ def run_pipeline_bench(args, build, model_config, kv_dtype=None):
     res_stage = stage.run(prompts, T, sp, S, seed=args.seed, hook=hook, watchdog=wd, stats_window=(t_a, t_b),
                           fault=fault)
     wd.beat("report")
+    if getattr(args, "dump_outputs", None) and res_stage.tokens is not None:
+        # bench.py --dump-outputs: the rank that owns the sampled ids writes them (float32, exact for
+        # token ids): every id of every sequence, and those of the last timed step (column W + K)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        toks = np.asarray(res_stage.tokens, dtype=np.float32)
+        np.save(os.path.join(args.dump_outputs, "tokens.npy"), toks)
+        last = np.ascontiguousarray(toks[:, min(W + K, toks.shape[1] - 1)])
+        np.save(os.path.join(args.dump_outputs, "last_tokens.npy"), last)
     fdt = torch.float64
     dt = torch.tensor([marks[t_b] - marks[t_a], marks[t_p] - marks[0]], device=cdev, dtype=fdt)
     dist.all_reduce(dt, op=dist.ReduceOp.MAX)

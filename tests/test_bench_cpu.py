@@ -42,6 +42,45 @@ def test_bench_single_cpu(lanes):
     assert d["config"]["lanes"] == lanes
 
 
+def test_bench_full_gates_side_points_cpu():
+    """A plain run measures only the headline; the batch-1 latency point (a decode run of its own)
+    comes with --full."""
+    base = [sys.executable, "bench.py", *COMMON, "--lanes", "1", "--latency-point", "int8"]
+    plain = subprocess.run(base, cwd=ROOT, capture_output=True, text=True, timeout=300)
+    full = subprocess.run(base + ["--full"], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert plain.returncode == 0 and full.returncode == 0, (plain.stderr[-1500:], full.stderr[-1500:])
+    p, f = _last_json(plain.stdout), _last_json(full.stdout)
+    assert REQUIRED <= set(p) and "latency_point" not in p and "one_lane_point" not in p
+    assert REQUIRED <= set(f) and f["latency_point"]["micro_batch"] == 1
+    assert f["latency_point"]["w8a8_smoothquant"]["p50_ms"] > 0
+
+
+@pytest.mark.parametrize("lanes", [1, 2])
+def test_bench_dump_outputs_cpu(tmp_path, lanes):
+    """--dump-outputs writes the timed path's outputs as float32 .npy files, identical from run to
+    run with the same arguments; --steps sets the number of timed steps (token columns)."""
+    import numpy as np
+    dumps = []
+    for name in ("a", "b"):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, "bench.py", *COMMON, "--lanes", str(lanes), "--dump-outputs", str(d)],
+                           cwd=ROOT, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-3000:]
+        res = _last_json(r.stdout)
+        assert res["steps"] == 3 and res["ms_per_step"] > 0
+        assert abs(res["ms_per_step"] * res["steps"] * res["value"] / 1e3 - 2 * lanes * 3) < 0.01 * 2 * lanes * 3
+        dumps.append({p.stem: np.load(p) for p in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert set(a) == {"tokens", "last_tokens", "next_logits", "logit_rows"} == set(b)
+    B = 2 * lanes
+    assert a["tokens"].shape == (B, 1 + 1 + 3)                 # prefill token + 1 warm-up + 3 timed steps
+    assert a["last_tokens"].shape == (B,) and (a["last_tokens"] == a["tokens"][:, -1]).all()
+    assert a["next_logits"].shape[0] == a["logit_rows"].shape[0] == B and np.isfinite(a["next_logits"]).all()
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for k in a:
+        assert a[k].dtype == np.float32 and np.array_equal(a[k], b[k]), k
+
+
 def test_bench_metrics_out_and_tracing_cpu(tmp_path):
     """--metrics-out appends the result record; EDGELLM_TRACE / EDGELLM_SYNC_DEBUG paths run."""
     path = tmp_path / "m.jsonl"
@@ -95,6 +134,21 @@ def test_bench_self_launch_cpu(n):
     d = json.loads(lines[0])
     assert REQUIRED <= set(d) and d["n_gpus"] == n and d["world_size"] == n and len(d["per_rank"]) == n
     assert d["config"]["parallelism"] == f"pp{n}" and d["value"] > 0
+
+
+def test_bench_pipeline_dump_outputs_cpu(tmp_path):
+    """--dump-outputs in the pipeline: the rank that owns the sampled ids writes them (float32)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    cmd = [sys.executable, "bench.py", "--gpus", "2", *COMMON, "--lanes", "1", "--dump-outputs", str(tmp_path / "d")]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _last_json(r.stdout)
+    toks, last = np.load(tmp_path / "d" / "tokens.npy"), np.load(tmp_path / "d" / "last_tokens.npy")
+    assert toks.dtype == last.dtype == np.float32 and toks.shape[0] == d["config"]["global_batch"]
+    # prefill token, 1 warm-up step, 3 timed steps (the last of them is column 4), one step past the window
+    assert toks.shape[1] == 6 and np.array_equal(last, toks[:, 4])
+    assert ((toks >= 0) & (toks < 512) & (toks == np.round(toks))).all()
 
 
 def test_bench_self_launch_killed_rank_cpu(tmp_path):
